@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- Ed448 variable-base scalarmuls/s, batch 2^20 per GPU (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the line: the headline figure, per_gpu and the
+config it ran.  --full adds everything else below (the parity check of the timed outputs, roofline, configs,
+end_to_end, cpu_baseline).  --dump-outputs DIR writes what the last timed step computed (rank 0's; see dump_outputs).
 
 N > 1 works both ways: launched as `python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N ...` (RANK/LOCAL_RANK/WORLD_SIZE in the environment), or plainly as `python bench.py --gpus
@@ -18,6 +22,7 @@ Rank 0 prints ONE JSON line.
 
 Objects on the line besides the driver's contract:
   per_gpu       each rank's own throughput, device and average kernel time (config 5 asks for it)
+  (--full only, from here on)
   roofline      HBM roofline of the timed kernel: algorithmic bytes per op x ops per
                 launch / average launch duration from HIP events on the launch stream, against 8 TB/s.
                 The path is integer-multiply bound, so this fraction is tiny by construction;
@@ -122,6 +127,10 @@ def parse(argv=None):
     ap.add_argument("--log2-batch", type=int, default=LOG2_BATCH, help="operations per GPU (weak scaling)")
     ap.add_argument("--global-log2-batch", type=int, default=None,
                     help="one global batch of 2^G operations cut into contiguous per-rank slices (strong scaling)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity check of its outputs, roofline, configs, end_to_end and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64 / float32, exact)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the extra BASELINE configs on the default run")
     ap.add_argument("--workload", default="varbase", choices=sorted(WORKLOADS))
@@ -171,7 +180,8 @@ SAMPLE = 256   # lanes of every config the oracle re-computes in the cpu_baselin
 
 def make_workload(name, cx, access):
     """-> dict(step, kernel, check() -> (ok, text, extra), sample() -> what the oracle needs to re-compute
-    the first SAMPLE lanes (host arrays only; the oracle itself is touched in cpu_baseline_leg alone)).
+    the first SAMPLE lanes (host arrays only; the oracle itself is touched in cpu_baseline_leg alone), outputs: the
+    device arrays a caller of the timed entry point receives, one row per operation).
     access: "index-independent" | "fast" -- passed to every timed call as its GOLDILOCKS_AMD_CALL_TABLES_* flags."""
     ga, np, torch, n, stream = cx.ga, cx.np, cx.torch, cx.n, cx.stream
     ct = access == "index-independent"
@@ -205,7 +215,7 @@ def make_workload(name, cx, access):
             m = min(n, SAMPLE)
             return dict(kind="varbase", bases=host(bases[:m]).view(np.uint64), scalars=host(scalars[:m]).view(np.uint64),
                         got=ga.point_encode_batch(host(out[:m]).view(np.uint64)))
-        return dict(step=step, kernel="k_point_scalarmul_ct", check=check, sample=sample)   # (the ladder in both table-access modes since round 6)
+        return dict(step=step, kernel="k_point_scalarmul_ct", check=check, sample=sample, outputs={"points": out})   # (the ladder in both table-access modes since round 6)
     if name in ("fixed", "base"):
         _, scalars = cx.pairs()
         out = torch.empty((n, 32), dtype=torch.int64, device="cuda")
@@ -237,7 +247,7 @@ def make_workload(name, cx, access):
             m = min(n, SAMPLE)
             return dict(kind="fixed", scalars=host(scalars[:m]).view(np.uint64),
                         got=ga.point_encode_batch(host(out[:m]).view(np.uint64)))
-        return dict(step=step, kernel=kernel, check=check, sample=sample, keep=[tab])
+        return dict(step=step, kernel=kernel, check=check, sample=sample, keep=[tab], outputs={"points": out})
     if name == "direct":       # wire format in and out: 56-byte encodings, decode + ladder + encode fused
         bases, scalars = cx.pairs()
         enc_in = torch.empty((n, 56), dtype=torch.uint8, device="cuda")
@@ -254,7 +264,7 @@ def make_workload(name, cx, access):
             ga.dev("point_encode", ref_enc.data_ptr(), ref.data_ptr(), n, None)
             ok = bool((ref_enc == enc_out).all()) and int((st_direct == -1).sum()) == n
             return ok, "every output equals encode(point_scalarmul(decode(input))) computed by the separate kernels", {}
-        return dict(step=step, kernel="k_direct_scalarmul_ct", check=check)
+        return dict(step=step, kernel="k_direct_scalarmul_ct", check=check, outputs={"encodings": enc_out, "status": st_direct})
     import _gen
     if name in ("sign", "x448"):
         nb = 57 if name == "sign" else 56
@@ -274,7 +284,7 @@ def make_workload(name, cx, access):
                 ga.dev("ed448_verify", st.data_ptr(), sig_out.data_ptr(), pk.data_ptr(), msg.data_ptr(), None, 32, 0,
                        None, 0, n, None)
                 return int((st == -1).sum()) == n, "every signature verifies (ed448_verify kernel)", {}
-            return dict(step=step, kernel="k_ed448_sign_ct" if ct else "k_ed448_sign", check=check)
+            return dict(step=step, kernel="k_ed448_sign_ct" if ct else "k_ed448_sign", check=check, outputs={"signatures": sig_out})
         pub = torch.empty((n, 56), dtype=torch.uint8, device="cuda")
         ga.dev("x448", pub.data_ptr(), None, None, sk.data_ptr(), n, None)
         peer = pub.view(n // 2, 2, 56).flip(1).reshape(n, 56).contiguous()      # lane i meets lane i^1's public key
@@ -286,7 +296,7 @@ def make_workload(name, cx, access):
             pairs = shared.view(n // 2, 2, 56)
             ok = bool((pairs[:, 0] == pairs[:, 1]).all()) and int((st448 == -1).sum()) == n
             return ok, "Diffie-Hellman symmetry: X448(a, pub_b) == X448(b, pub_a) for every neighbour pair", {}
-        return dict(step=step, kernel="k_x448", check=check)
+        return dict(step=step, kernel="k_x448", check=check, outputs={"shared_secrets": shared, "status": st448})
     # verify: signatures over 32-byte messages from 1024 distinct keys, produced by the
     # library's own derive/sign kernels (bit-exact vs the reference: tests/test_gpu_parity.py); 1 % corrupted
     v = verify_inputs(cx, distinct=name == "verify_distinct")
@@ -308,7 +318,7 @@ def make_workload(name, cx, access):
     # (the key-comb verification is a first pass, S*B computed ahead beside the combs' build, and a finish kernel: the
     # step's memory traffic is the three kernels' together; `kernel` names the dominant one)
     if name == "verify_distinct":
-        return dict(step=step, kernel="k_ed448_verify", check=check, sample=sample)
+        return dict(step=step, kernel="k_ed448_verify", check=check, sample=sample, outputs={"status": status})
     # ... and which comb the batch's keys got decides the first pass's kernel: asked of the library after the steps)
     def kernels_after():
         teeth = ga.last_verify_key_counts(teeth=True)[3]
@@ -320,7 +330,7 @@ def make_workload(name, cx, access):
         macs = V["macs_key_comb" + tag] + V["macs_per_key_comb" + tag] * V["keys"] // n
         return main, (main,) + VERIFY_STEP_KERNELS, macs
     return dict(step=step, kernel="k_ed448_verify_keycomb_xwide", check=check, sample=sample, kernels_after=kernels_after,
-                traffic_kernels=("k_ed448_verify_keycomb_xwide",) + VERIFY_STEP_KERNELS)
+                traffic_kernels=("k_ed448_verify_keycomb_xwide",) + VERIFY_STEP_KERNELS, outputs={"status": status})
 
 
 # the kernels of a key-comb verification step besides its main one (their traffic and instructions are summed into the
@@ -641,6 +651,30 @@ class ClockSampler:
         return v[len(v) // 2] if v else None
 
 
+# ---------------------------------------------------------------------------------------- --dump-outputs
+
+DUMP_MAX_BYTES = 60 * 10 ** 6          # (the dump is to stay under 64 MB)
+DUMP_SEED = 0x6475_6d70
+
+
+def dump_outputs(directory, outputs, n, np, torch):
+    """The arrays a caller of the timed entry point holds after the last timed step, as DIR/<name>.npy: one row per
+    operation, every value exact -- 64-bit words as their two 32-bit halves (low half first) in float64, 32-bit words in
+    float64, bytes in float32.  When all n rows would not fit in DUMP_MAX_BYTES, the same fixed, seeded sample of rows is
+    taken from every array.  DIR/lanes.npy holds the indices of the rows written."""
+    rows = {k: t.reshape(n, -1) for k, t in outputs.items()}
+    per_row = 8 + sum(t.shape[1] * {1: 4, 4: 8, 8: 16}[t.element_size()] for t in rows.values())
+    m = min(n, (DUMP_MAX_BYTES - 4096 * (len(rows) + 1)) // per_row)      # (4096: room for each file's header)
+    lanes = np.arange(n) if m == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "lanes.npy"), lanes.astype(np.float64))
+    for name, t in rows.items():
+        a = (t if m == n else t[torch.from_numpy(lanes).to(t.device)]).cpu().numpy()
+        if a.dtype.itemsize == 8:
+            a = a.view(np.uint32)
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64))
+
+
 # ---------------------------------------------------------------------------------------- one rank
 
 def time_workload(torch, shard, w, steps, warmup, dist, backend, clock=None):
@@ -844,18 +878,20 @@ def run_rank(args):
     w = make_workload(name, cx, args.table_access)
     pci_of = torch.cuda.get_device_properties(torch.cuda.current_device())
     pci_txt = "%04x:%02x:%02x" % (getattr(pci_of, "pci_domain_id", 0), getattr(pci_of, "pci_bus_id", 0), getattr(pci_of, "pci_device_id", 0))
-    clock = ClockSampler(pci_txt)
+    clock = ClockSampler(pci_txt) if args.full else None
     mine, worst, kernel_ms = time_workload(torch, shard, w, args.steps, args.warmup, dist, backend, clock)
-    if "kernels_after" in w:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w["outputs"], n, np, torch)
+    if args.full and "kernels_after" in w:
         w["kernel"], w["traffic_kernels"], w["macs"] = w["kernels_after"]()
     avg_ms = sum(kernel_ms) / len(kernel_ms)
     # (each rank's device by its PCI address: a first real 8-GPU run shows at a glance that eight ranks sit on eight devices)
     props = torch.cuda.get_device_properties(device)
     pci = [getattr(props, k, -1) for k in ("pci_domain_id", "pci_bus_id", "pci_device_id")]
     rows = shard.gather_over_ranks([rank, device, n * args.steps / mine, avg_ms, n, lo] + pci, dist, backend)
-    ok, check, extra = w["check"]() if rank == 0 else (True, "n/a", {})
+    ok, check, extra = w["check"]() if rank == 0 and args.full else (True, "n/a", {})
     default_line = rank == 0 and world == 1 and name == "varbase" and args.table_access == "index-independent" \
-        and args.global_log2_batch is None
+        and args.global_log2_batch is None and args.full
     samples = {}
 
     line = None
@@ -878,20 +914,21 @@ def run_rank(args):
                        "base_table_bits": ga.get_base_table_bits(),
                        # what the library holds on the device after the timed steps (workspace + staging + tables)
                        "device_memory_bytes": ga.device_info()["workspace_bytes"],
-                       "parity_spot_check": "ok" if ok else "FAILED", "check": check},
+                       "parity_spot_check": ("ok" if ok else "FAILED") if args.full else "not run (--full)", "check": check},
             # the code object this line was measured on and what compiled it (parity evidence is tied to both)
             "build": ga.build_info(),
             "per_gpu": [dict({"rank": int(r[0]), "device": int(r[1]), "value": r[2], "unit": spec["unit"],
                               "kernel_ms_avg": r[3], "batch": int(r[4]),
                               "pci": "%04x:%02x:%02x" % (int(r[6]), int(r[7]), int(r[8])) if r[6] >= 0 else None},
                              **({"slice": [int(r[5]), int(r[5]) + int(r[4])]} if scaling == "strong" else {})) for r in rows],
-            "roofline": roofline(name, w["kernel"], n, avg_ms, args.table_access, w.get("traffic_kernels"), ga.get_base_table_bits(), w.get("macs"),
-                                 clock.sustained_mhz()),
         }
-        line["roofline"]["kernel_ms_every_step"] = [round(x, 3) for x in kernel_ms]   # (rank 0's; HIP events on the launch stream)
-        line.update(extra)
-        if "sample" in w and world == 1:
-            samples["headline"] = w["sample"]()
+        if args.full:
+            line["roofline"] = roofline(name, w["kernel"], n, avg_ms, args.table_access, w.get("traffic_kernels"),
+                                        ga.get_base_table_bits(), w.get("macs"), clock.sustained_mhz())
+            line["roofline"]["kernel_ms_every_step"] = [round(x, 3) for x in kernel_ms]   # (rank 0's; HIP events on the launch stream)
+            line.update(extra)
+            if "sample" in w and world == 1:
+                samples["headline"] = w["sample"]()
 
     # the other BASELINE configs, a few steps each (default single-GPU run of the headline only)
     if default_line and not args.no_configs:
@@ -942,7 +979,7 @@ def run_rank(args):
         line["end_to_end"], e2e_ok = end_to_end(cx)
         ok = ok and e2e_ok
 
-    if rank == 0 and world == 1 and name == "varbase" and not args.no_cpu_baseline:   # rank 0 at N = 1 only
+    if args.full and rank == 0 and world == 1 and name == "varbase" and not args.no_cpu_baseline:   # rank 0 at N = 1 only
         bases, scalars = cx.pairs()
         b_h, s_h = bases.cpu().numpy().view(np.uint64), scalars.cpu().numpy().view(np.uint64)
         line["cpu_baseline"], checks = cpu_baseline_leg(np, b_h, s_h, samples)

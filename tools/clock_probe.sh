@@ -4,7 +4,7 @@
 # rocm-smi is sampled twice a second for the whole life of a 600-step run; every distinct reading of every device is printed once.
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT"
-python bench.py --workload varbase --steps 600 --warmup 3 --no-cpu-baseline --no-configs --no-end-to-end > /tmp/clock_probe_bench.json 2>/dev/null &
+python bench.py --full --workload varbase --steps 600 --warmup 3 --no-cpu-baseline --no-configs --no-end-to-end > /tmp/clock_probe_bench.json 2>/dev/null &
 PID=$!
 : > /tmp/clock_samples.txt
 while kill -0 $PID 2>/dev/null; do

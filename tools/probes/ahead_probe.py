@@ -18,7 +18,7 @@ for p in range(passes):
     for lib in libs:
         for rounds, hashed in configs:
             env = dict(os.environ, GOLDILOCKS_AMD_LIB=lib, GOLDILOCKS_AMD_AHEAD_ROUNDS=str(rounds), GOLDILOCKS_AMD_AHEAD_HASH=str(hashed))
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "verify", "--steps", "30", "--no-cpu-baseline",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "verify", "--steps", "30", "--no-cpu-baseline",
                                 "--no-configs", "--no-end-to-end"], env=env, capture_output=True, text=True)
             try:
                 line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -19,7 +19,7 @@ for p in range(passes):
         if names and name not in names:
             continue
         env = dict(os.environ, GOLDILOCKS_AMD_LIB=lib)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-end-to-end"], env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-end-to-end"], env=env, capture_output=True, text=True)
         try:
             line = json.loads(r.stdout.strip().splitlines()[-1])
             print("pass %d %-10s headline %.3f ms  " % (p, name, line["ms_per_step"]) +

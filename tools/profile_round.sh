@@ -16,15 +16,15 @@ mkdir -p "$OUT" "$DST"
 cd /tmp && export TMPDIR=/tmp
 BENCH="$ROOT/bench.py"
 FAST="--table-access fast"            # the opt-in for public scalars; bench.py's default is the library's (index-independent)
-Q="--no-cpu-baseline --no-configs --no-end-to-end"
+Q="--full --no-cpu-baseline --no-configs --no-end-to-end"
 
 # the driver's command: headline + configs + cpu_baseline on one line (written at the end, with this library's counters)
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_default" -- \
-    python3 "$BENCH" --steps 5 --warmup 1 > "$OUT/stats_default.log" 2>&1
+    python3 "$BENCH" --full --steps 5 --warmup 1 > "$OUT/stats_default.log" 2>&1
 # ... and without its end_to_end leg (which runs the same kernels in one-residency chunks): per-kernel averages of
 # full-size launches only, comparable with the line's kernel_ms_avg figures
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_defaultresident" -- \
-    python3 "$BENCH" --steps 5 --warmup 1 --no-end-to-end > "$OUT/stats_defaultresident.log" 2>&1
+    python3 "$BENCH" --full --steps 5 --warmup 1 --no-end-to-end > "$OUT/stats_defaultresident.log" 2>&1
 
 for wl in varbase fixed base verify verify_distinct sign x448 direct; do
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$wl" -- \
@@ -82,7 +82,7 @@ python3 "$ROOT/tools/summarize_prof.py" "$OUT" "$DST"
 # the bench lines once more, now that the counters of THIS library are in place (bench.py reports `traffic` and `valu_issue`
 # only from counters stamped with the current kernel sources: the lines above were written before there were any)
 cp "$DST/pmc_traffic.json" "$ROOT/profiles/pmc_traffic.json"
-python3 "$BENCH" > "$DST/bench_default.json" 2> "$OUT/bench_default.err"
+python3 "$BENCH" --full > "$DST/bench_default.json" 2> "$OUT/bench_default.err"
 for wl in varbase fixed base verify verify_distinct sign x448 direct; do
     python3 "$BENCH" --workload $wl $Q > "$DST/bench_$wl.json" 2> "$OUT/bench_$wl.err"
 done
